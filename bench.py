@@ -6,6 +6,11 @@ NVIDIA-format HDF5 shards read through the native loader, fused Adam,
 --fast-stat-sync (as in every documented reference run), weak scaling.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype fp32|bf16] [--hetero 2,6]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs with
+``--dump-outputs`` and prints the result line; ``--full`` adds the measurements that take runs of
+their own (the all-reduce bus bandwidth of a data-parallel job).
 
 Launch modes (one process per GPU, RCCL over xGMI):
 
@@ -101,9 +106,18 @@ def parse():
     p.add_argument("--gemm-choices", default=None,
                    help="JSON of measured GEMM engine choices: loaded if it exists (no measuring in warm-up), "
                         "else written after the run (profiling runs use it to keep tuning out of the trace)")
-    return p.parse_args()
-
-
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last one computed as DIR/<name>.npy: the step's "
+                        "logged statistics, the gradient norm, and a fixed seeded sample of the updated parameters "
+                        "and of their gradient (same arguments -> same inputs, so two builds compare output for output)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline figure (data-parallel runs on the native "
+                        "engine: the bus bandwidth of a 64 MB all-reduce per rank); a plain run only sets up, "
+                        "warms up, times --steps steps and prints the result line")
+    b = p.parse_args()
+    if b.steps < 1 or b.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return b
 
 
 def _free_port():
@@ -309,7 +323,7 @@ def run_rank(b):
     if b.gemm_choices and os.path.exists(b.gemm_choices):
         G.load_choices(b.gemm_choices)
     ctl.optimizer  # build optimizer/scheduler (and the DP engine) before timing
-    comm_id = _comm_identity(ctl, world, rank)
+    comm_id = _comm_identity(ctl, world, rank, busbw=b.full)
     emul = None
     if b.emulate_world and b.emulate_world > 1:
         comm = getattr(ctl.model, "comm", None)
@@ -356,7 +370,7 @@ def run_rank(b):
             time.sleep(b.host_delay_us * 1e-6)
         h0 = time.perf_counter()
         data_wait += h0 - d0
-        ctl.train_step(batch)
+        last = ctl.train_step(batch)
         host += time.perf_counter() - h0
     if b.sync_debug:
         torch.cuda.set_sync_debug_mode(0)
@@ -380,6 +394,8 @@ def run_rank(b):
     from hetseq_amd.ops import bert_ops
 
     bert_ops.check_device_errors()
+    if b.dump_outputs and rank == 0:
+        _dump_outputs(b.dump_outputs, ctl, last)
     sec = elapsed / b.steps
     seqs = b.batch * b.update_freq * world
     me = {"rank": rank, "local_rank": local_rank, "group": int(os.environ.get("HETSEQ_GROUP", "0")),
@@ -652,11 +668,12 @@ _AB = {
 }
 
 
-def _comm_identity(ctl, world, rank):
+def _comm_identity(ctl, world, rank, busbw=False):
     """Per rank, before timing: the PCI bus id of the device it runs on and -- on the native engine --
-    what RCCL itself reports for the communicator (ncclCommCount / ncclCommUserRank / its device) and
-    the bus bandwidth of a 64 MB all-reduce.  Rank 0 checks that the job is N ranks on N DISTINCT
-    devices and that RCCL saw N ranks 0..N-1 (a misconfigured launch fails here, not in the result)."""
+    what RCCL itself reports for the communicator (ncclCommCount / ncclCommUserRank / its device) and,
+    with ``busbw`` (--full), the bus bandwidth of a 64 MB all-reduce.  Rank 0 checks that the job is N
+    ranks on N DISTINCT devices and that RCCL saw N ranks 0..N-1 (a misconfigured launch fails here,
+    not in the result)."""
     import torch
     import torch.distributed as dist
 
@@ -667,7 +684,8 @@ def _comm_identity(ctl, world, rank):
     comm = getattr(ctl.model, "comm", None)
     if comm is not None:
         me.update(comm.identity())
-        me["allreduce_64mb_busbw_gbs"] = comm.busbw(64 << 20)
+        if busbw:
+            me["allreduce_64mb_busbw_gbs"] = comm.busbw(64 << 20)
     ids = [me]
     if world > 1:
         ids = [None] * world
@@ -709,6 +727,43 @@ def _host_phases(ctl):
     timed(ctl, "_prepare_sample", "prepare_sample")
     timed(ctl, "_set_seed", "set_seed")
     return acc
+
+
+DUMP_SAMPLE = 1 << 22  # elements of the flat parameter / gradient buffers written by --dump-outputs (16 MB each)
+
+
+def _dump_outputs(outdir, ctl, logging_output):
+    """--dump-outputs: what the last timed train_step handed its caller -- the logging output it
+    returned (loss and nll_loss as logged: over sample_size ln 2; ntokens, nsentences), the update's
+    gradient norm (after the 1 / sample_size scale, before clipping), and the state it left: the updated
+    fp32 parameters and the gradient buffer they were updated from (the backward's sum; scale and clip
+    are applied inside the update).  The two flat buffers (110 M floats each for BERT-base) are sampled
+    at DUMP_SAMPLE fixed positions (seeded, ascending, the same for every run of a given model)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(outdir, exist_ok=True)
+    ctl.store.params_ready()  # (a staged update may still be writing the last chunks)
+    torch.cuda.synchronize()
+
+    def host(v):
+        return float(v.item()) if torch.is_tensor(v) else float(v)
+
+    stats = np.array([host((logging_output or {}).get(k, float("nan")))
+                      for k in ("loss", "nll_loss", "ntokens", "nsentences")], dtype=np.float64)
+    np.save(os.path.join(outdir, "step_stats.npy"), stats)
+    np.save(os.path.join(outdir, "grad_norm.npy"), np.array([host(ctl._prev_grad_norm)], dtype=np.float64))
+    n = ctl.store.param.numel()
+    if n > DUMP_SAMPLE:  # one position in each of DUMP_SAMPLE equal strides: distinct, ascending, all regions covered
+        stride = n // DUMP_SAMPLE
+        idx = np.arange(DUMP_SAMPLE, dtype=np.int64) * stride + np.random.RandomState(20240607).randint(
+            0, stride, size=DUMP_SAMPLE, dtype=np.int64)
+        idx = torch.from_numpy(idx).to(ctl.store.param.device)
+        pick = lambda t: t.index_select(0, idx)
+    else:
+        pick = lambda t: t
+    np.save(os.path.join(outdir, "params.npy"), pick(ctl.store.param).float().cpu().numpy())
+    np.save(os.path.join(outdir, "grads.npy"), pick(ctl.store.grad).float().cpu().numpy())
 
 
 _CTL = [None]  # the controller of an --ab run (variants that switch its state)

@@ -83,6 +83,16 @@ def test_gpus_must_match_world_size():
     assert rc == 2 and "disagrees with --hetero" in err
 
 
+def test_plain_run_options():
+    """``--full`` and ``--dump-outputs DIR`` are accepted; ``--steps`` is the number of timed steps, so
+    a run without one is refused (exit 2) instead of dividing by it."""
+    rc, ranks, _ = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--dump-outputs", "out",
+                         "--dry-run", "-1"])
+    assert rc == 0 and len(ranks) == 1
+    rc, ranks, err = _run(["--steps", "0", "--dry-run", "-1"])
+    assert rc == 2 and not ranks and "--steps" in err
+
+
 # ------------------------------------------------------------------ agreed native-comm fallback
 def _fallback_worker(rank, world, path, fault, q):
     import torch
