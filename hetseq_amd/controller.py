@@ -94,6 +94,7 @@ class Controller(object):
         self._graph = None  # runtime.graphs.GraphedStep once --hip-graph captured the update
         self._scale_buf = None  # fp32 device scalar: the gradient scale of the fast-stat path
         self._graph_warmup = 3  # eager updates first: GEMM autotuning, TunableOp, allocator warm-up
+        self._valid_batches = {}  # validation subset -> its frozen batches (get_valid_iterator)
         self.init_meters(args)
 
     def init_meters(self, args):
@@ -260,6 +261,71 @@ class Controller(object):
             required_batch_size_multiple=self.args.required_batch_size_multiple, seed=self.args.seed,
             num_shards=self.args.distributed_world_size, shard_id=self.args.distributed_rank,
             num_workers=self.args.num_workers, epoch=epoch, device=self.device if self.cuda else None)
+
+    # ------------------------------------------------------------------ validation
+    def get_valid_iterator(self, subset):
+        """This rank's share of ``subset`` in a fixed order: batches of --max-sentences-valid /
+        --max-tokens-valid, sharded by rank as the training batches are, never shuffled, always
+        epoch 1.  (Built here, not through the task's per-dataset iterator cache: the training
+        iterator of the same dataset keeps its own batches and position.)"""
+        from hetseq_amd.data import data_utils, iterators
+
+        dataset = self.task.dataset(subset)
+        batches = self._valid_batches.get(subset)
+        if batches is None:
+            batches = data_utils.batch_by_size(
+                dataset.ordered_indices(), dataset.num_tokens,
+                max_tokens=getattr(self.args, "max_tokens_valid", None) or self.args.max_tokens,
+                max_sentences=getattr(self.args, "max_sentences_valid", None) or self.args.max_sentences,
+                required_batch_size_multiple=self.args.required_batch_size_multiple)
+            batches = self._valid_batches[subset] = tuple(batches)
+        itr = iterators.EpochBatchIterator(dataset=dataset, collate_fn=dataset.collater, batch_sampler=batches,
+                                           seed=self.args.seed, num_shards=self.args.distributed_world_size,
+                                           shard_id=self.args.distributed_rank, num_workers=self.args.num_workers,
+                                           epoch=0, device=self.device if self.cuda else None)
+        return itr.next_epoch_itr(shuffle=False)
+
+    def validate(self, subset):
+        """One pass over ``subset``: the task's set-level metrics (an OrderedDict of floats).
+
+        Every batch adds its sums into ONE device accumulator (Task.valid_step: forward only, no host
+        synchronisation, no collective), so ranks with fewer batches -- uneven shards, heterogeneous
+        launches -- simply finish early; then one all-reduce of the accumulator and one host read.
+        The bare model runs, not the data-parallel wrapper (no gradient hooks, no bucket traffic).
+        Gradient buffers, RNG state, the update count and the model's train / eval mode are left as
+        found; a pending staged optimizer update is waited for first."""
+        model = self.get_model()
+        self.store.params_ready()  # (the staged update of the last step may still be writing parameters)
+        if hasattr(self.task, "prepare_model_for_valid"):
+            self.task.prepare_model_for_valid(model, subset)
+        was_training = model.training
+        if was_training:
+            model.eval()
+        acc = self.task.valid_acc(self.device)
+        try:
+            with torch.no_grad():
+                for sample in self.get_valid_iterator(subset):
+                    sample = self._prepare_sample(sample)
+                    if sample is None:  # (a padded shard's empty batch)
+                        continue
+                    self.task.valid_step(sample, model, acc)
+        finally:
+            if was_training:
+                model.train()
+        if self._sync_stats():
+            if isinstance(self.model, FlatDDP):
+                self.model.all_reduce_(acc)  # native engine: in-stream RCCL
+            else:
+                dist.all_reduce(acc)
+        host = acc.tolist()  # the pass's one host read
+        if self.cuda:
+            from hetseq_amd.ops import bert_ops
+
+            bert_ops.check_device_errors(self.device)  # e.g. more labelled rows than the validation capacity
+        metrics = self.task.valid_metrics(host)
+        self.meters["valid_loss"].reset()
+        self.meters["valid_loss"].update(metrics["loss"], max(metrics.get("nsentences", 1.0), 1.0))
+        return metrics
 
     # ------------------------------------------------------------------ training
     def train_step(self, samples, dummy_batch=False, raise_oom=False):

@@ -97,6 +97,9 @@ int launch_attn_bwd(int, const void*, const int64_t*, const float*, const void*,
 void launch_xent_fwd(int, const void*, const int64_t*, int, int, int64_t, int, float*, float*, float*, hipStream_t);
 void launch_xent_bwd(int, void*, const int64_t*, const float*, int, int, int64_t, int, const float*, const float*,
                      hipStream_t, float*);
+// score.hip
+int launch_mlm_nsp_score(int, const void*, const int64_t*, int, int, int64_t, int, int, const float*, const int64_t*, int,
+                         float*, int32_t*, double*, hipStream_t);
 // gemm.hip
 int gemm_last_ksplit();
 void set_h3_occ3(int on);
@@ -696,6 +699,17 @@ PYBIND11_MODULE(_hip, m) {
   }, pybind11::arg("dt"), pybind11::arg("logits"), pybind11::arg("labels"), pybind11::arg("lse"), pybind11::arg("rows"),
      pybind11::arg("V"), pybind11::arg("ldv"), pybind11::arg("ignore"), pybind11::arg("dloss"), pybind11::arg("stats"),
      pybind11::arg("st"), pybind11::arg("amax") = 0);
+  m.def("mlm_nsp_score", [](int dt, i64 logits, i64 labels, int rows, int V, i64 ldv, int ignore, int k, i64 nsp_logits,
+                            i64 nsp_labels, int B, i64 row_loss, i64 rank, i64 acc, i64 st) {
+    pre_launch("mlm_nsp_score");
+    if (rows < 0 || B < 0 || V < 1 || ldv < V) throw std::invalid_argument("mlm_nsp_score: rows, B >= 0, 1 <= V <= ldv");
+    const int rc = launch_mlm_nsp_score(dt, P(const void*, logits), P(const int64_t*, labels), rows, V, ldv, ignore, k,
+                                        P(const float*, nsp_logits), P(const int64_t*, nsp_labels), B,
+                                        P(float*, row_loss), P(int32_t*, rank), P(double*, acc), ST(st));
+    check_launch("mlm_nsp_score");
+    return rc;
+  }, "validation scoring (score.hip): acc[8] += {mlm loss sum, n, top-1, top-k, nsp loss sum, n, correct, sentences} "
+     "of fp32 MLM logits [rows, V] (row stride ldv) and NSP logits [B, 2]; -1: a dtype it does not serve");
 
   // returns 0 when launched, -1 when the shape/epilogue is not served (caller falls back)
   m.def("set_skip_launches", [](int mask) { hs::g_hs_skip = mask; },

@@ -904,6 +904,7 @@ class BertForPreTraining(BertPreTrainedModel):
         self.cls = BertPreTrainingHeads(config, self.bert.embeddings.word_embeddings.weight)
         self.apply(self.init_bert_weights)
         self.max_predictions_per_seq = None  # set by the task from the data (sparse MLM capacity)
+        self.max_predictions_per_seq_valid = None  # the same for validation forwards (score)
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, masked_lm_labels=None,
                 next_sentence_label=None, checkpoint_activations=False):
@@ -919,6 +920,33 @@ class BertForPreTraining(BertPreTrainedModel):
             return mlm_scores, nsp_scores
         return (_xent(mlm_scores.reshape(-1, self.config.vocab_size), masked_lm_labels.reshape(-1), -1)
                 + _xent(nsp_scores.reshape(-1, 2), next_sentence_label.reshape(-1), -1))
+
+    def score(self, input_ids, token_type_ids, attention_mask, masked_lm_labels, next_sentence_label, acc, k=5):
+        """Validation: add this batch's masked-LM / NSP loss sums and hit counts into ``acc``
+        (ops/score.py: its layout and the tie rule).  Forward only, dropout off, no autograd graph, no
+        host synchronisation.  The fused path (every GEMM engine, both compute dtypes) scores the head's
+        own logits with the HIP scoring kernels; otherwise the module graph feeds the torch scoring.
+        The sparse head's row capacity is ``max_predictions_per_seq_valid`` (the validation data's, set
+        by the task; None: every position)."""
+        from hetseq_amd.ops.score import mlm_nsp_score_
+
+        was_training = self.training
+        if was_training:
+            self.eval()
+        try:
+            with torch.no_grad():
+                if self.bert._can_fuse(input_ids):
+                    self._fused_loss(input_ids, token_type_ids, attention_mask, masked_lm_labels, next_sentence_label,
+                                     False, score=(acc, k))
+                else:
+                    mlm_scores, nsp_scores = self(input_ids, token_type_ids, attention_mask)
+                    mlm_nsp_score_(acc, mlm_scores.reshape(-1, self.config.vocab_size).float(),
+                                   masked_lm_labels.reshape(-1), nsp_scores.reshape(-1, 2).float(),
+                                   next_sentence_label.reshape(-1), k=k)
+        finally:
+            if was_training:
+                self.train()
+        return acc
 
     def grad_groups(self):
         return self.bert.grad_groups()
@@ -1052,7 +1080,10 @@ class BertForPreTraining(BertPreTrainedModel):
         return ([e.word_embeddings.weight, e.position_embeddings.weight, e.token_type_embeddings.weight],
                 [e.LayerNorm.weight, e.LayerNorm.bias])
 
-    def _fused_loss(self, input_ids, token_type_ids, attention_mask, labels, nsp_label, checkpoint_activations):
+    def _fused_loss(self, input_ids, token_type_ids, attention_mask, labels, nsp_label, checkpoint_activations,
+                    score=None):
+        """``score``: None (training), or (accumulator, k) of a validation forward -- the head then also
+        scores its logits (ops/score.py) and sizes the sparse rows for the validation data."""
         from hetseq_amd.ops.bert_ops import FusedPreTrainingLoss
 
         if token_type_ids is None:
@@ -1067,7 +1098,8 @@ class BertForPreTraining(BertPreTrainedModel):
         pool, plan = self.bert._amax_plan(extra_weights=head_w, extra_slots=3)
         seq2d = self.bert.fused_encoder(input_ids, token_type_ids, attention_mask, checkpoint_activations,
                                         amax=(pool, plan))
-        cap = B * S if self.max_predictions_per_seq is None else min(B * S, B * int(self.max_predictions_per_seq))
+        max_pred = self.max_predictions_per_seq if score is None else self.max_predictions_per_seq_valid
+        cap = B * S if max_pred is None else min(B * S, B * int(max_pred))
         if head_hp is not None or head_bf is not None:
             cap = (cap + 127) // 128 * 128  # (rows past the labelled ones: zero rows, label -1, no loss / gradient)
         t, pred = self.cls.predictions.transform, self.cls.predictions
@@ -1079,6 +1111,8 @@ class BertForPreTraining(BertPreTrainedModel):
             meta["h3p"] = head_hp
         if head_bf is not None:
             meta["bf16pad"] = head_bf
+        if score is not None:
+            meta["score"] = score
         if pool is not None and head_w:
             L = len(plan)
             last = plan[-1]

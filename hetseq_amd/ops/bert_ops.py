@@ -1216,6 +1216,11 @@ class FusedPreTrainingLoss(torch.autograd.Function):
                            bn.data_ptr(), nsp_labels.data_ptr(), out.data_ptr(), pooled.data_ptr(),
                            nsp_logits.data_ptr(), nsp_lse.data_ptr(), stats.data_ptr(), stats[2:].data_ptr(),
                            stream_handle())
+        score = meta.get("score")  # validation: (accumulator, k) -- ops/score.py scores the same logits
+        if score is not None:
+            from hetseq_amd.ops.score import mlm_nsp_score_
+
+            mlm_nsp_score_(score[0], logits, lab, nsp_logits, nsp_labels, k=score[1])
         ctx.padded = lbuf is not None
         ctx.bfp = meta.get("bf16pad") if (hpw is None and lbuf is not None and t2.dtype == torch.bfloat16) else None
         ctx.save_for_backward(idx, lab, hsel, t1pre, t1, z, mean, rstd, t2,

@@ -26,6 +26,8 @@ change a reference default):
   --no-gemm-tuning          skip the measured GEMM selection table
   --deterministic           bitwise-reproducible mode (fixed RCCL algorithm, deterministic torch ops)
   --hip-graph               replay the captured update as one HIP graph (launch-bound configurations)
+  --validate                score --valid-subset every --validate-interval epochs (dataset group; off by default)
+  --validate-interval-updates N  and every N updates
 """
 from __future__ import annotations
 
@@ -75,6 +77,12 @@ def add_dataset_args(parser, train=False, gen=False, task="bert"):
                            help="comma separated list of data subsets to use for validation")
         group.add_argument("--validate-interval", type=int, default=1, metavar="N", help="validate every N epochs")
         group.add_argument("--disable-validation", action="store_true", help="disable validation")
+        group.add_argument("--validate", action="store_true",
+                           help="score --valid-subset (held-out loss and accuracies) at the end of every "
+                                "--validate-interval-th epoch; the value of --best-checkpoint-metric drives the "
+                                "lr scheduler and checkpoint_best.pt (off by default: the reference never validates)")
+        group.add_argument("--validate-interval-updates", type=int, default=0, metavar="N",
+                           help="also validate every N updates (0 = never; implies validation)")
         group.add_argument("--max-tokens-valid", type=int, metavar="N",
                            help="maximum number of tokens in a validation batch (defaults to --max-tokens)")
         group.add_argument("--max-sentences-valid", type=int, metavar="N",
@@ -285,7 +293,17 @@ def parse_args_and_arch(parser, s=None):
         args.max_sentences_valid = args.max_sentences
     if hasattr(args, "max_tokens_valid") and args.max_tokens_valid is None:
         args.max_tokens_valid = args.max_tokens
+    if validation_enabled(args) and getattr(args, "hip_graph", False):
+        parser.error("--hip-graph cannot be combined with --validate / --validate-interval-updates: validation "
+                     "runs eagerly between updates, and a pass between replays of the captured update is not "
+                     "supported")
     return args
+
+
+def validation_enabled(args):
+    """Validation runs when asked for (--validate or --validate-interval-updates N) and not disabled."""
+    asked = getattr(args, "validate", False) or getattr(args, "validate_interval_updates", 0) > 0
+    return bool(asked) and not getattr(args, "disable_validation", False)
 
 
 def get_pre_parser():

@@ -92,6 +92,22 @@ class Task(object):
     def update_step(self, num_updates):
         pass
 
+    # ------------------------------------------------------------------ validation
+    def valid_acc(self, device):
+        """A zeroed device accumulator for one validation pass (float64 sums; the task defines the layout)."""
+        return torch.zeros(8, dtype=torch.float64, device=device)
+
+    def valid_step(self, sample, model, acc):
+        """Add one batch's sums into ``acc`` on the device: no host synchronisation, no collective."""
+        raise NotImplementedError("task {} does not define validation".format(type(self).__name__))
+
+    def valid_metrics(self, acc_host):
+        """Set-level metrics from the (all-reduced) accumulator's host values."""
+        raise NotImplementedError("task {} does not define validation".format(type(self).__name__))
+
+    def prepare_model_for_valid(self, model, split):
+        pass
+
 
 class LanguageModelingTask(Task):
     """BERT pre-training on NVIDIA-format HDF5 shards."""
@@ -141,6 +157,29 @@ class LanguageModelingTask(Task):
         if ds is not None and hasattr(model, "max_predictions_per_seq"):
             model.max_predictions_per_seq = int(getattr(ds, "num_pred", 0)) or None
 
+    def prepare_model_for_valid(self, model, split):
+        """The sparse MLM head's capacity for validation forwards: the validation data's own."""
+        ds = self.datasets.get(split)
+        if ds is not None and hasattr(model, "max_predictions_per_seq_valid"):
+            model.max_predictions_per_seq_valid = int(getattr(ds, "num_pred", 0)) or None
+
+    def valid_acc(self, device):
+        from hetseq_amd.ops.score import score_acc
+
+        return score_acc(device)
+
+    def valid_step(self, sample, model, acc, k=5):
+        """acc += [mlm_loss_sum, mlm_n, mlm_top1, mlm_topk, nsp_loss_sum, nsp_n, nsp_correct, nsentences]."""
+        model.score(*sample[:5], acc, k=k)
+        return acc
+
+    def valid_metrics(self, acc_host):
+        """loss (= mlm_loss + nsp_loss, nats), mlm_loss, nsp_loss, mlm_ppl, mlm_acc, mlm_acc5, nsp_acc,
+        nsentences: means over the whole set, whatever the batch size or the number of ranks."""
+        from hetseq_amd.ops.score import metrics
+
+        return metrics(acc_host)
+
 
 class MNISTTask(Task):
     def __init__(self, args):
@@ -165,6 +204,25 @@ class MNISTTask(Task):
         self.datasets[split] = dataset
         print("| loading finished")
         return dataset
+
+    def valid_step(self, sample, model, acc):
+        """acc += [nll_sum, n, correct, 0...] (the model's own evaluation mode: summed NLL, hits)."""
+        x, y = sample[0], sample[1]
+        with torch.no_grad():
+            loss, correct = model(x, y, eval=True)
+        acc[0] += loss.detach().to(torch.float64)
+        acc[1] += float(y.numel())
+        acc[2] += correct.detach().to(torch.float64)
+        return acc
+
+    def valid_metrics(self, acc_host):
+        a = [float(v) for v in acc_host]
+        n = max(a[1], 1.0)
+        out = collections.OrderedDict()
+        out["loss"] = a[0] / n
+        out["accuracy"] = 100.0 * a[2] / n
+        out["nsentences"] = a[1]
+        return out
 
 
 class BertTokenClassificationTask(Task):

@@ -90,7 +90,10 @@ def main(args, init_distributed=False):
            and (epoch_itr.epoch < max_epoch or (epoch_itr.epoch == max_epoch and epoch_itr.resuming))
            and controller.get_num_updates() < max_update):
         train(args, controller, task, epoch_itr)
-        valid_losses = [None]
+        if options.validation_enabled(args) and epoch_itr.epoch % args.validate_interval == 0:
+            valid_losses = validate(args, controller, task, epoch_itr, args.valid_subset.split(","))
+        else:
+            valid_losses = [None]
         lr = controller.lr_step(epoch_itr.epoch, valid_losses[0])
         if epoch_itr.epoch % args.save_interval == 0:
             checkpoint_utils.save_checkpoint(args, controller, epoch_itr, valid_losses[0])
@@ -135,10 +138,40 @@ def train(args, controller, task, epoch_itr):
             controller.get_meter("wps").reset()
             controller.get_meter("ups").reset()
         num_updates = controller.get_num_updates()
+        valid_losses = [None]
+        if (options.validation_enabled(args) and getattr(args, "validate_interval_updates", 0) > 0
+                and num_updates % args.validate_interval_updates == 0 and num_updates > 0):
+            valid_losses = validate(args, controller, task, epoch_itr, args.valid_subset.split(","))
         if (args.save_interval_updates > 0 and num_updates % args.save_interval_updates == 0 and num_updates > 0):
-            checkpoint_utils.save_checkpoint(args, controller, epoch_itr, None, end_of_epoch=False)
+            checkpoint_utils.save_checkpoint(args, controller, epoch_itr, valid_losses[0], end_of_epoch=False)
         if num_updates >= max_update:
             break
+
+
+def validate(args, controller, task, epoch_itr, subsets):
+    """Score every subset of ``subsets`` (Controller.validate: one device accumulator, one collective
+    and one host read per subset) and log it; returns, per subset, the value of
+    --best-checkpoint-metric -- what the lr scheduler and the best-checkpoint logic compare."""
+    valid_losses = []
+    for subset in subsets:
+        metrics = controller.validate(subset)
+        stats = collections.OrderedDict(metrics)
+        stats["num_updates"] = controller.get_num_updates()
+        key = args.best_checkpoint_metric
+        if key not in metrics:
+            raise ValueError("--best-checkpoint-metric {}: the task reports {}".format(key, ", ".join(metrics)))
+        best = getattr(checkpoint_utils.save_checkpoint, "best", None)
+        pick = max if args.maximize_best_checkpoint_metric else min
+        stats["best_" + key] = metrics[key] if best is None else pick(best, metrics[key])
+        progress = progress_bar.build_progress_bar(args, [], epoch_itr.epoch,
+                                                   prefix="valid on '{}' subset".format(subset),
+                                                   no_progress_bar="simple")
+        progress.print(stats, tag="valid", step=controller.get_num_updates())
+        # (--json-log: one record per pass, its keys prefixed so they never read as training stats)
+        progress.log(collections.OrderedDict(("valid_" + k, v) for k, v in stats.items()), tag="valid",
+                     step=controller.get_num_updates())
+        valid_losses.append(metrics[key])
+    return valid_losses
 
 
 def get_training_stats(controller):

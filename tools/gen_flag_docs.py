@@ -14,7 +14,7 @@ from hetseq_amd import options  # noqa: E402
 
 def rows(parser):
     for g in parser._action_groups:
-        acts = [a for a in g._group_actions if not isinstance(a, argparse._HelpAction)]
+        acts = [a for a in g._group_actions if not isinstance(a, argparse._HelpAction) and a.help != argparse.SUPPRESS]
         if not acts:
             continue
         yield g.title, acts
